@@ -21,7 +21,10 @@ Timing: W untimed warm-up steps; then every rank passes a barrier, synchronises 
 times exactly K steps ending with its own device synchronisation; the reported time is the MAX of
 the per-rank times (one gloo max-reduction AFTER the clock stops -- no collective or barrier inside
 the timed region other than the step's own gradient all-reduces).
-With a communicator the JSON carries ``comm_profile``: the RCCL world, the latency of each bucket's
+A plain run does only that: set-up, the start-up schedule calibration, warm-up, the timed steps, the
+``--dump-outputs`` files when asked for, the result line.  ``--full`` adds what the headline figure
+does not need: ``--acc-steps`` further untimed steps and the top-1 read-out on the test split, and,
+with a communicator, ``comm_profile``: the RCCL world, the latency of each bucket's
 standalone all-reduce, and the exposed communication (step with the plan's collectives minus the
 local schedule without any, interleaved replays).
 
@@ -87,11 +90,20 @@ def parse(argv=None):
     ap.add_argument("--synthetic-mode", default="hard", choices=["easy", "hard"],
                     help="synthetic data generator (hard, the default: stronger noise / affine jitter, so the top-1 "
                          "read-out carries information; easy saturates at 1.0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed --acc-steps and the top-1 "
+                         "read-out on the test split, and with a communicator the comm_profile measurements.  A plain "
+                         "run sets up, calibrates the schedule, warms up, times the steps and prints the result line")
     ap.add_argument("--eval", action="store_true", default=True)
     ap.add_argument("--acc-steps", type=int, default=500,
-                    help="untimed training steps after the timed region and before the top-1 read-out (so the "
-                         "accuracy in the JSON is that of a trained model, not of warm-up + K steps)")
-    ap.add_argument("--no-eval", dest="eval", action="store_false")
+                    help="--full: untimed training steps after the timed region and before the top-1 read-out (so "
+                         "the accuracy in the JSON is that of a trained model, not of warm-up + K steps)")
+    ap.add_argument("--no-eval", dest="eval", action="store_false", help="--full without the top-1 read-out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left a caller as DIR/<name>.npy "
+                         "(float32 / float64): params, momentum (the flat parameter and SGD-momentum slabs) and "
+                         "metrics ([loss_sum, correct, count] over warm-up + timed steps).  Rank 0 writes; the "
+                         "replicas are identical.  Inputs are seeded: same arguments, same inputs")
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--digest", action="store_true",
                     help="every rank prints a sha256 of its final parameters to stderr (replica consistency check)")
@@ -226,6 +238,18 @@ def timed_region(ctx, tr, run, steps: int, cuda_sync, clock=time.perf_counter) -
     return ctx.all_reduce_max(t1 - t0)
 
 
+def dump_outputs(d: str, tr, train) -> None:
+    """``--dump-outputs``: the state the last timed step left behind, as a caller of the step reads it -- the flat
+    fp32 parameter slab (``state_dict()`` is a view of it), the SGD-momentum slab, and the device-accumulated
+    metrics [loss_sum, correct, count] of warm-up + timed steps.  ~0.5 MB (LeNet-5) / ~1 MB (MLP): no sampling."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    tr.synchronize()
+    np.save(os.path.join(d, "params.npy"), tr.params.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "momentum.npy"), tr.mom.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "metrics.npy"), np.array([train.loss_sum, train.correct, train.count], dtype=np.float64))
+
+
 def main(argv=None) -> int:
     a = parse(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -258,7 +282,8 @@ def main(argv=None) -> int:
         print(f"[bench] note: --gpus {a.gpus} but WORLD_SIZE={ctx.world}; using {ctx.world}", file=sys.stderr)
     W, rank, dev = ctx.world, ctx.rank, ctx.device
 
-    acc_steps = max(0, a.acc_steps) if a.eval else 0
+    do_eval = a.full and a.eval
+    acc_steps = max(0, a.acc_steps) if do_eval else 0
     images, labels, idx_all, test_x, test_y = bench_data(W, rank, a.batch, a.warmup + a.steps + acc_steps,
                                                          a.synthetic_mode)
     load = None
@@ -323,7 +348,7 @@ def main(argv=None) -> int:
         # the external data plane runs the eager phase API (forward_backward -> host all-reduce -> SGD), not
         # the captured schedules a calibration would time: nothing to choose
         tune = {"chosen": "eager-phases", "timings_ms": {}, "note": "external data plane: no graph schedules"}
-    if (comm is not None or oneshot is not None) and use_graph:
+    if a.full and (comm is not None or oneshot is not None) and use_graph:
         prof = tr.comm_profile(reduce_max=ctx.all_reduce_max, tune=tune, probe=probe)
         if oneshot is None and W > 1:
             prof["oneshot_probe"] = "validated (measure-only)" if probe is not None else (probe_err or "not probed")
@@ -341,9 +366,11 @@ def main(argv=None) -> int:
     elapsed = timed_region(ctx, tr, run, a.steps, lambda: torch.cuda.synchronize(dev))
     train = tr.read_metrics()
     tr.check_comm()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr, train)
 
     top1 = None
-    if a.eval:
+    if do_eval:
         if acc_steps:
             run(acc_steps)  # untimed: the model the top-1 describes has trained warm-up + K + acc_steps steps
         ev = tr.evaluate(torch.from_numpy(test_x.reshape(-1, 784)), torch.from_numpy(test_y),

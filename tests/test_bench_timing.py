@@ -70,6 +70,32 @@ def test_timed_region_elapsed_is_per_rank_clock():
     assert seen == [out] and out > 0
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    assert bench.parse(["--full"]).full is True and bench.parse(["--full"]).eval is True
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import torch
+
+    from pytorch_ddp_mnist_amd.engine.native import EpochStats
+
+    log = _Log()
+    tr = FakeTrainer(log)
+    tr.params = torch.arange(7, dtype=torch.float32)
+    tr.mom = -torch.arange(7, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "o"), tr, EpochStats(12.5, 3.0, 8.0))
+    assert log == ["sync"]                                # the stream is drained before the slabs are read
+    got = {p.name: np.load(p) for p in sorted((tmp_path / "o").iterdir())}
+    assert sorted(got) == ["metrics.npy", "momentum.npy", "params.npy"]
+    assert got["params.npy"].dtype == np.float32 and got["momentum.npy"].dtype == np.float32
+    assert got["metrics.npy"].dtype == np.float64
+    assert np.array_equal(got["params.npy"], np.arange(7)) and np.array_equal(got["momentum.npy"], -np.arange(7.0))
+    assert got["metrics.npy"].tolist() == [12.5, 3.0, 8.0]
+
+
 def test_resolve_plan():
     assert resolve_plan("auto") is None and resolve_plan(None) is None
     assert resolve_plan("fixed") == "join"              # no calibration, default plan (no KeyError)

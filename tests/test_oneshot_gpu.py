@@ -76,8 +76,8 @@ def test_oneshot_two_ranks_share_one_gpu(native, tmp_path, plan):
     from test_shared_gpu_ranks import _emulate
     steps, warmup, batch = 4, 2, 2048
     out, err = _bench(["--gpus", "2", "--comm", "gloo", "--allreduce", "oneshot", "--batch", str(batch),
-                       "--steps", str(steps), "--warmup", str(warmup), "--no-eval", "--digest", "--plan", plan,
-                       "--dump-params", str(tmp_path / "p")], log_dir=tmp_path / "ranks")
+                       "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-eval", "--digest",
+                       "--plan", plan, "--dump-params", str(tmp_path / "p")], log_dir=tmp_path / "ranks")
     assert out["n_gpus"] == 2 and out["allreduce"] == "oneshot" and out["value"] > 0
     assert "one-shot" in out["config"]["comm"]
     assert out["config"]["plan"]["plan"] == ("join" if plan == "fixed" else "overlap")
@@ -128,7 +128,7 @@ def test_oneshot_and_rccl_profile_world1(native):
     """World 1 with both data planes: the step runs the one-shot kernel, and comm_profile reports the standalone
     latency of each collective on BOTH (RCCL all-reduce and one-shot)."""
     out, _ = _bench(["--comm-world1", "--allreduce", "oneshot", "--batch", "1024", "--steps", "8", "--warmup", "2",
-                     "--no-eval"])
+                     "--full", "--no-eval"])
     prof = out["comm_profile"]
     assert prof["rccl_world"] == 1 and prof["allreduce"] == "oneshot"
     for c in prof["collectives"]:

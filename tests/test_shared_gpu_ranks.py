@@ -99,7 +99,7 @@ def test_comm_profile_world1(native, model):
     """With a (world-1) RCCL communicator the JSON attributes the communication: RCCL world, each
     collective's standalone all-reduce latency and the exposed comm (plan step - local step)."""
     out, _ = _bench(["--comm-world1", "--model", model, "--batch", "1024", "--steps", "8", "--warmup", "2",
-                     "--no-eval"])
+                     "--full", "--no-eval"])
     assert out["rccl_world"] == 1
     prof = out["comm_profile"]
     assert prof["rccl_world"] == 1
