@@ -76,6 +76,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("metric_rows", [](int B) { return metric_rows(B); });
   m.attr("L1_SPLIT_MAX_B") = L1_SPLIT_MAX_B;
   m.attr("STAMP_ROWS") = STAMP_ROWS;
+  m.def("wgrad_sk_mode", &wgrad_sk_mode);  // read-only: what this process read from MNIST_AMD_WGRAD_SK
+  m.attr("SK_MIN_B") = SK_MIN_B;
 #ifdef MNIST_AMD_F32_SPLIT
   m.attr("F32_SPLIT") = 3;  // fp32 products as exact 3-part bf16 splits on 16x16x32 MFMAs (common.h Mma<float>, opt-in build)
 #else

@@ -1297,7 +1297,7 @@ __global__ __launch_bounds__(256) void wgrad_sgd_kernel(WgArgs<T> a) {
 // wgrad_lds_kernel from B >= SK_MIN_B).  Same 64x64 output blocks, batch splits and slab layout as wgrad_kernel,
 // but each of the 4 waves computes the WHOLE 64x64 block (4x4 MFMA tiles, 64 accumulators) over every 4th
 // K-step of the workgroup's batch range, and the four partial blocks are summed through LDS in a fixed order
-// ((w0 + w1) + (w2 + w3)) before the one slab row is written.  Against wgrad_kernel (four 32x32 quadrants per
+// ((w0 + w2) + (w1 + w3)) before the one slab row is written.  Against wgrad_kernel (four 32x32 quadrants per
 // block, every fragment fetched by two waves): half the L2 -> CU fragment traffic, 16 instead of 4 MFMAs per
 // 8 fragment loads, and a quarter of the dependent K-steps per wave -- SK_PF steps (8 x SK_PF fragments) are
 // issued before the first MFMA, so a whole 512-row split is ONE memory round trip per wave (LeNet-5 / MLP at
@@ -1305,7 +1305,7 @@ __global__ __launch_bounds__(256) void wgrad_sgd_kernel(WgArgs<T> a) {
 // (profiles/r5_session1/pmc_table_final.md).
 // fp32 (SPL): the 4 A and 4 B fragments of a K-step are cut into bf16 hi / mid / lo parts ONCE and reused by the
 // 16 products (Mma<float>::mma_pp), instead of a cut per product.
-constexpr int SK_MIN_B = 2048;  // smallest batch on the split-K-in-workgroup kernel
+// (SK_MIN_B, launch.h: the smallest batch on this kernel)
 // PF: K-steps per wave whose fragments are in flight together (8 x PF 16-byte loads per lane)
 template <typename T, bool SPL, int PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF > 2 || (sizeof(T) == 4 && SPL) ? 2 : 3))) void wgrad_sk_kernel(WgArgs<T> a) {
@@ -1482,7 +1482,7 @@ int wgrad_sk_pf() {
 // B=8192 ~9.7 us span vs 15.9 us for wgrad_kernel alone, but beside conv_bwd its 32 KB of LDS per workgroup cannot
 // co-reside with conv_bwd's two 71 KB workgroups (the concurrent step 0.1068 vs 0.0975 ms); the MLP's LDS-staged
 // wgrad_lds_kernel stays faster (32.2 vs 35.6 us per step)
-int wgrad_sk_mode() {
+int wgrad_sk_env() {  // (public as wgrad_sk_mode, launch.h)
   static const int m = [] {
     const char* e = std::getenv("MNIST_AMD_WGRAD_SK");
     return e && *e ? (*e == '1' ? 1 : 0) : -1;
@@ -1513,7 +1513,7 @@ int wgrad_launch(const HeadBuffers& hb, int B, int splits, float* slab, int slab
   // fp32 MLP weight gradient as 3-part bf16 splits from B = 4096 on (MLP fp32 B=8192 -6 %, but B=1024 +6 %:
   // profiles/r5_session1/hsplit2); no effect for bf16 (wg_mma)
   const bool spl = B >= 4096;
-  const int skm = wgrad_sk_mode();
+  const int skm = wgrad_sk_env();
   // (off by default: on the chosen schedules the LDS-free wgrad_kernel runs beside conv_bwd, and giving the serial
   //  candidate a different kernel would end the bitwise equality of the single-GPU schedules)
   const bool sk = skm == 1;
@@ -1638,6 +1638,8 @@ __global__ __launch_bounds__(256) void gather_next_kernel(BatchRef br) {
 }
 
 }  // namespace
+
+int wgrad_sk_mode() { return wgrad_sk_env(); }
 
 void launch_gather_next(const BatchRef& br, hipStream_t s) {
   if (!br.xnext || br.batch_stride <= 0) return;

@@ -124,6 +124,10 @@ struct SgdFuse {
 int launch_head_wgrad(ModelKind m, DType t, const HeadBuffers& hb, int B, int splits, float* slab,
                       int slab_ld, hipStream_t s, int head_rows = 0, const SgdFuse* fuse = nullptr,
                       int job_mask = 7);
+// The opt-in split-K-in-workgroup weight gradient (head.hip wgrad_sk_kernel): MNIST_AMD_WGRAD_SK as this process
+// read it (1 = on, 0 = off, -1 = unset; read once), and the smallest batch launch_head_wgrad gives that kernel.
+int wgrad_sk_mode();
+constexpr int SK_MIN_B = 2048;
 
 void launch_lenet_conv_fwd(DType t, bool train, const BatchRef& br, const LenetConvBuffers& cb,
                            hipStream_t s);
@@ -131,7 +135,8 @@ void launch_lenet_conv_fwd(DType t, bool train, const BatchRef& br, const LenetC
 // replaces launch_lenet_conv_fwd + launch_head for bf16 batches B >= 4096, B % 16 == 0 (Trainer::set_fwd_head(false)
 // selects the two kernels).  Returns the head-rows value for launch_head_wgrad's XCD-aware mapping (32: the fused
 // kernel's 16-row units give each XCD the same contiguous eighth of the batch as 32-row head tiles), or 0
-// when it does not apply (the caller launches the two kernels).
+// when it does not apply (the caller launches the two kernels).  Like launch_lenet_head16 it runs rup(B, 32) / 16
+// tiles: a last tile without batch rows zero-fills the rows the bf16 weight gradient reads past a partial batch.
 int launch_lenet_fwd_head(DType t, const BatchRef& br, const LenetConvBuffers& cb, const HeadBuffers& hb,
                           hipStream_t s);
 bool lenet_fwd_head_applies(DType t, int B);

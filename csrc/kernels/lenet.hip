@@ -1693,7 +1693,10 @@ bool lenet_fwd_head_applies(DType t, int B) {
 
 int launch_lenet_fwd_head(DType t, const BatchRef& br, const LenetConvBuffers& cb, const HeadBuffers& hb, hipStream_t s) {
   if (!lenet_fwd_head_applies(t, br.B)) return 0;
-  const int grid = br.B / 16;
+  // 16-row tiles up to the bf16 weight gradient's 32-row K padding (wgrad.h Bp): when B % 32 == 16 (a partial last
+  // batch) the last tile has no batch row and only zero-fills rows [B, B + 16) of the transposed activations /
+  // gradients, which otherwise hold the previous batch and leaked into the FC weight gradient
+  const int grid = rup(br.B, 32) / 16;
   hipLaunchKernelGGL(fwd_head_kernel<bf16>, dim3(grid), dim3(512), 0, s, br, cb, hb);
   return 32;
 }
@@ -1701,7 +1704,9 @@ int launch_lenet_fwd_head(DType t, const BatchRef& br, const LenetConvBuffers& c
 int launch_lenet_head16(DType t, const BatchRef& br, const HeadBuffers& hb, hipStream_t s) {
   constexpr int maxb = 2048;  // largest batch for head16_kernel (the LDS-staged head_kernel above it)
   if (t != DType::BF16 || br.B <= 0 || br.B > maxb) return 0;
-  const int grid = (br.B + 15) / 16;
+  // as launch_lenet_fwd_head: tiles up to rup(B, 32), the rows the weight gradient reads (B % 32 in 1..16: one more
+  // tile, all of its rows past the batch, which zero-fills them)
+  const int grid = rup(br.B, 32) / 16;
   hipLaunchKernelGGL(head16_kernel<bf16>, dim3(grid), dim3(512), 0, s, br, hb);
   return (grid % 8 == 0 && br.B % 32 == 0) ? 32 : 16;  // wgrad XCD mapping: as launch_lenet_fwd_head
 }

@@ -339,16 +339,24 @@ def test_training_learns(native, small_mnist, model_name, dtype):
 
 
 @pytest.mark.parametrize("model_name,dtype", [("lenet5", "fp32"), ("mlp", "fp32"), ("lenet5", "bf16"), ("mlp", "bf16")])
-def test_eval_matches_torch(native, small_mnist, model_name, dtype):
-    """Forward-only eval loop (eval() semantics: no dropout) vs torch.  bf16: the oracle sees the
-    bf16-rounded inputs/weights; predictions may flip only on near-ties."""
+# 2048: the forward-only head runs 32-row tiles (128: 16-row tiles)
+@pytest.mark.parametrize("batch", [128, 2048])
+def test_eval_matches_torch(native, small_mnist, model_name, dtype, batch):
+    """Forward-only eval loop (eval() semantics: no dropout) vs torch, over one full chunk of the trainer batch
+    and a partial chunk of 300 rows.  bf16: the oracle sees the bf16-rounded inputs/weights; predictions may
+    flip only on near-ties."""
     x, y, xt, yt = small_mnist
-    torch.manual_seed(4)
+    # (a seed at which both models' fp32 oracle keeps every test row's top-2 logit margin above 1e-4, see below:
+    #  MLP 8.5e-4, LeNet-5 3.2e-2 over all 1024 rows)
+    torch.manual_seed(2084)
     module = build_model(model_name)
-    tr = make_trainer(model_name, dtype, 128, x, y, module, dropout=0.2)
-    ev = tr.evaluate(torch.from_numpy(xt.reshape(-1, 784)), torch.from_numpy(yt), torch.arange(300, dtype=torch.int32))
+    tr = make_trainer(model_name, dtype, batch, x, y, module, dropout=0.2)
+    n = batch + 300
+    rows = torch.arange(n, dtype=torch.int32) % len(yt)
+    ev = tr.evaluate(torch.from_numpy(xt.reshape(-1, 784)), torch.from_numpy(yt), rows)
+    assert ev.count == n
     m = copy.deepcopy(module).eval()
-    xx = _normalize(xt[:300])
+    xx = _normalize(xt[rows.numpy()])
     if dtype == "bf16":
         xx = bf16_round(xx)
         with torch.no_grad():
@@ -356,12 +364,16 @@ def test_eval_matches_torch(native, small_mnist, model_name, dtype):
                 if p.dim() > 1:
                     p.copy_(bf16_round(p))
     with torch.no_grad():
-        out = m(xx.view(300, 1, 28, 28) if model_name == "lenet5" else xx.view(300, -1))
-        yy = torch.from_numpy(yt[:300].astype(np.int64))
+        out = m(xx.view(n, 1, 28, 28) if model_name == "lenet5" else xx.view(n, -1))
+        yy = torch.from_numpy(yt[rows.numpy()].astype(np.int64))
         loss = (F.nll_loss(out, yy, reduction="sum") if model_name == "lenet5"
                 else F.cross_entropy(out, yy, reduction="sum")).item()
         corr = int((out.argmax(1) == yy).sum())
     if dtype == "fp32":
+        # the exact count is a condition on the inputs: no evaluated row may be a near-tie of its two top logits
+        top2 = out.topk(2, dim=1).values
+        margin = float((top2[:, 0] - top2[:, 1]).min())
+        assert margin > 1e-4, f"oracle's smallest top-2 logit margin {margin}: choose another seed"
         assert abs(ev.loss_sum - loss) / loss < 1e-4
         assert ev.correct == corr
     else:

@@ -65,8 +65,9 @@ def test_bucket_groups_bitwise_equal(native):
 
 @pytest.mark.timeout(900)
 def test_large_batch_schedules_bitwise_equal(native):
-    """The headline batch (8192: fused forward + head, split-K-in-workgroup weight gradient, 16 FC splits): serial,
-    concurrent, JOIN / SPLIT and multi-group SPLIT steps give bitwise-identical parameters."""
+    """The headline batch (8192: fused forward + head, the default wgrad_kernel / wgrad_lds_kernel weight gradient,
+    16 FC splits): serial, concurrent, JOIN / SPLIT and multi-group SPLIT steps give bitwise-identical parameters.
+    (The opt-in split-K-in-workgroup weight gradient, MNIST_AMD_WGRAD_SK=1, is not run here: test_wgrad_sk_gpu.py.)"""
     extra = ("--batch", "8192", "--steps", "2")
     serial = _digests({"MNIST_AMD_CONCURRENT": "0"}, ["local"], extra=extra)
     d = _digests({"MNIST_AMD_CONCURRENT": "1"}, ["local", "join", "split", "split_g0.1.2", "split_g01.2"], extra=extra)
