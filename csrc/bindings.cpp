@@ -230,7 +230,10 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("has_overlap", &Trainer::has_overlap)
       .def_property_readonly("has_oneshot", &Trainer::has_oneshot)
       .def("set_world", &Trainer::set_world)
-      .def("set_optimizer", &Trainer::set_optimizer)
+      .def("set_optimizer", &Trainer::set_optimizer, py::arg("lr"), py::arg("momentum"), py::arg("weight_decay") = 0.f,
+           py::arg("nesterov") = false)
+      .def("set_lr_table", &Trainer::set_lr_table, py::arg("table"), py::arg("n"), py::arg("cell"))
+      .def_property_readonly("has_lr_table", &Trainer::has_lr_table)
       .def("set_dropout", &Trainer::set_dropout)
       .def("set_buckets", &Trainer::set_buckets)
       .def_property("comm_enabled", &Trainer::comm_enabled, &Trainer::set_comm_enabled)

@@ -205,6 +205,47 @@ constexpr float MNIST_NORM_A = (float)(1.0 / (255.0 * 0.3081));
 constexpr float MNIST_NORM_B = (float)(-0.1307 / 0.3081);
 DEV float mnist_norm(uint32_t u8) { return __builtin_fmaf(float(u8), MNIST_NORM_A, MNIST_NORM_B); }
 
+// torch.optim.SGD (dampening 0) for ONE parameter, the recurrence of every update site (optim.hip's three kernels
+// and the wgrad_sgd_tile epilogue, wgrad.h), after the DDP average is folded into g:
+//   g += wd * p ;  b = mu * m + g (stored to *mom) ;  d = nesterov ? g + mu * b : b ;  returns p - lr * d
+// mom == null: no momentum buffer (d = g).  wd, mu and nesterov are launch arguments, so both branches are
+// wave-uniform; with wd == 0 and nesterov == 0 the arithmetic is exactly  b = mu * m + g ; p - lr * b.
+// The two optional terms are explicit fmas on the ROUNDED g: at most sites g is itself a product (sum * scale,
+// grad * 1/W), and left to the compiler's contraction  g + wd * p  became fma(sum, scale, wd * p) at one site and
+// fma(wd, p, g) at another -- JOIN no longer bitwise the local step.
+DEV float sgd_update(float p, float g, float m, float* mom, float lr, float mu, float wd, int nesterov) {
+  if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+  if (mom) {
+    const float b = (wd != 0.f || nesterov) ? __builtin_fmaf(mu, m, g) : mu * m + g;  // (default: as it always was)
+    *mom = b;
+    if (nesterov) g = __builtin_fmaf(mu, b, g);
+    else g = b;
+  }
+  return p - lr * g;
+}
+
+// The step's learning rate for an update kernel: the schedule's published cell when there is one (launch.h
+// SgdHyper::lr_dev), else the launch argument.  A relaxed ATOMIC load: the compiler merged a plain one with the
+// kernel-argument load of `lr` into one FLAT load of a selected address, and a flat load in flight turns every later
+// s_waitcnt vmcnt(N) into vmcnt(0) -- wgrad_sgd_kernel's staged K-step waits all became full drains (MLP fp32 B=128
+// 19.3 -> 19.6 us per step on the default path).
+DEV float sgd_lr(const float* lr_dev, float lr) {
+  return lr_dev ? __hip_atomic_load(const_cast<float*>(lr_dev), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : lr;
+}
+
+// The rate of the step whose global index is step_ptr[1] into the schedule's cell (launch.h LrSched; one lane of a
+// training head kernel, see HeadBuffers::lr_sched for why there and only there).
+template <class Sched>
+DEV void publish_lr(const Sched* sc, const int32_t* step_ptr) {
+  // the two pointers come from memory, so the compiler takes them for generic ones: cast to global, or the load
+  // and the store are FLAT operations, after which every s_waitcnt vmcnt(N) of the head kernel is a full drain
+  typedef __attribute__((address_space(1))) float gfloat;
+  const Sched d = *sc;
+  const gfloat* table = (const gfloat*)d.table;
+  gfloat* cell = (gfloat*)d.cell;
+  *cell = table[max(min(step_ptr[1], d.n - 1), 0)];
+}
+
 DEV int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // wave-level reductions (64 lanes)

@@ -485,6 +485,10 @@ __global__ __launch_bounds__(NWV * 64) void head_kernel(BatchRef br, HeadBuffers
   stamp(1);
   // labels: fetched by the LAST threads of the block (idle in L1 when NWV > NT1), used after 3 barriers
   const int gstep = EARLY_STEP ? gstep_early : br.step_ptr[1];  // dropout stream (see batch_idx)
+  // a learning-rate schedule: this step's rate for its update kernels (launch.h HeadBuffers::lr_sched), training only
+  if constexpr (TRAIN) {
+    if (hb.lr_sched && blockIdx.x == 0 && tid == 0) publish_lr(hb.lr_sched, br.step_ptr);
+  }
   if (!look) {
     const int t = tid - (NTH - R);
     if (t >= 0) {

@@ -32,6 +32,13 @@ struct BatchRef {
 // after the step counter was set from the host).
 void launch_gather_next(const BatchRef& br, hipStream_t s);
 
+// A learning-rate schedule as the head kernels see it (device memory, written by Trainer::set_lr_table)
+struct LrSched {
+  const float* table;  // [n] float32 rates indexed by the global step; steps >= n use the last one
+  float* cell;         // the current step's rate, read by the update kernels
+  int32_t n;
+};
+
 struct HeadBuffers {
   const float* params;   // fp32 master slab
   const void* pack;      // packed T operands
@@ -52,6 +59,16 @@ struct HeadBuffers {
   int32_t xcd = 0;       // the head kernel used the XCD-contiguous row mapping (BatchRef::xcd)
   int32_t ablate = 0;    // diagnostics only (MNIST_AMD_HEAD_ABLATE): bit 0 = skip the X^T stores (wrong wgrad)
   const uint8_t* yb = nullptr;  // LeNet head16: this step's labels in batch order (LenetConvBuffers::yb) or null
+  // Learning-rate schedule (null: none, no store): the TRAINING launch of a head-family kernel publishes
+  // *cell = table[min(step_ptr[1], n - 1)] from one lane of workgroup 0 (common.h publish_lr).  The head is the one
+  // point of a step that is stream-ordered after every update of the previous step (join_aux) and before every
+  // update of its own, so the update kernels read the cell (SgdHyper::lr_dev) instead of indexing the table with a
+  // counter that other update kernels of the same step are bumping.  ONE pointer to a device-resident descriptor,
+  // not its three fields: fwd_head_kernel sits at its SGPR and VGPR caps, and five more kernel-argument SGPRs held
+  // through it cost six SGPR spills and one more spilled VGPR in the compiler's resource report (as did the one
+  // pointer when the store sat at the kernel's end; next to the label read, where the step counter is in use
+  // anyway, the report is the parent's: 106 SGPRs, 128 VGPRs, 4 spilled).
+  const LrSched* lr_sched = nullptr;
 };
 
 struct LenetConvBuffers {
@@ -110,8 +127,17 @@ int launch_head(ModelKind m, DType t, bool train, const BatchRef& br, const Head
 // the whole gradient): g = scale * dW, momentum, parameter, packed operand images and the device step
 // counters updated in place -- the separate reduce + SGD kernel and its boundary disappear.  Bitwise
 // equal to the wgrad -> reduce_sgd pair (a one-slab reduce is scale * dW).
+// The optimizer's hyper-parameters as every update kernel takes them, by value (constants of a run):
+// torch.optim.SGD(lr, momentum, dampening=0, weight_decay, nesterov); common.h sgd_update is the recurrence.
+struct SgdHyper {
+  float lr = 0.f, momentum = 0.f, weight_decay = 0.f;
+  int32_t nesterov = 0;
+  const float* lr_dev = nullptr;  // a schedule's current rate (HeadBuffers::lr_now), read once at kernel start; null: lr
+};
+
 struct SgdFuse {
-  float scale, lr, momentum;
+  float scale;
+  SgdHyper h;
   float* params;
   float* grad;
   float* mom;
@@ -169,11 +195,11 @@ void launch_reduce(const float* slab, int slab_ld, int nslab, int p0, int p1, fl
 // `skip`: optional device word (a one-shot all-reduce's latched error, oneshot.hip): when it reads non-zero the
 // parameters and momentum are left as they are (the gradient may hold a partial sum); the step counter still moves.
 void launch_sgd_pack(ModelKind m, DType t, float* params, const float* grad, float* mom, void* pack,
-                     int nparam, float lr, float momentum, float gscale, int32_t* step_ptr,
+                     int nparam, const SgdHyper& h, float gscale, int32_t* step_ptr,
                      hipStream_t s, const uint32_t* skip = nullptr);
 // Same, over the parameter range [p0, p1) only (per-bucket updates of the split multi-GPU plan).
 void launch_sgd_pack_range(ModelKind m, DType t, float* params, const float* grad, float* mom, void* pack, int p0,
-                           int p1, float lr, float momentum, float gscale, int32_t* step_ptr, hipStream_t s,
+                           int p1, const SgdHyper& h, float gscale, int32_t* step_ptr, hipStream_t s,
                            const uint32_t* skip = nullptr);
 void launch_pack(ModelKind m, DType t, const float* params, void* pack, int nparam, hipStream_t s);
 // Bounded device busy-wait (watchdog tests).
@@ -181,7 +207,7 @@ void launch_spin(double seconds, hipStream_t s);
 // Fused gradient reduce + SGD + pack + step bump (no all-reduce between them: single-GPU runs).
 void launch_reduce_sgd(ModelKind m, DType t, const float* slab_a, int lda, int na, const float* slab_b, int ldb,
                        int nb, int split, int p0, int n, float scale, float* params, float* grad, float* mom,
-                       void* pack, float lr, float momentum, int32_t* step_ptr, hipStream_t s);  // params [p0, n)
+                       void* pack, const SgdHyper& h, int32_t* step_ptr, hipStream_t s);  // params [p0, n)
 
 void launch_gather_normalize(DType t, const BatchRef& br, void* out, int ld, hipStream_t s);
 

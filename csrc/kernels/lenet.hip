@@ -710,6 +710,9 @@ DEV void head16_tile(const BatchRef& br, const HeadBuffers& hb, char* ht, T* sX,
       lab = id >= 0 ? (int)br.labels[id] : 0;
     }
   }
+  // a learning-rate schedule: this step's rate for its update kernels (launch.h HeadBuffers::lr_sched; this tile
+  // body runs in training launches only)
+  if (hb.lr_sched && tile == 0 && tid == 0) publish_lr(hb.lr_sched, br.step_ptr);
   // sX complete (caller), `ht` free: a raw barrier after the LDS writes drained -- __syncthreads() would also
   // wait (vmcnt(0)) for the weight fragments just issued
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

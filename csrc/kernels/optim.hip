@@ -4,7 +4,8 @@
 //                 no float atomics).  Replaces the per-parameter .grad accumulation + the DDP
 //                 Reducer's bucket copy (survey N6/N9); `scale` carries the 1/B of the mean loss.
 //  sgd_pack     : p -= lr * (mu*buf + g/W) over the flat fp32 master slab (torch SGD semantics,
-//                 dampening 0, ddp_tutorial_cpu.py:61), 1/W of DDP averaging folded in, then the
+//                 dampening 0, ddp_tutorial_cpu.py:61; weight decay and Nesterov momentum when set:
+//                 common.h sgd_update), 1/W of DDP averaging folded in, then the
 //                 updated value is re-packed into the compute-dtype MFMA operand images
 //                 (models.h) and the device step counters are advanced.  Replaces the
 //                 _foreach_add_ multi-tensor apply (survey K15) plus any weight cast kernels.
@@ -101,20 +102,16 @@ __global__ __launch_bounds__(256) void reduce_direct_kernel(const float* __restr
 template <class Model, typename T>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(float* __restrict__ params, const float* __restrict__ grad,
                                                        float* __restrict__ mom, T* __restrict__ pack, int p0, int n,
-                                                       float lr, float mu, float gscale, int32_t* step_ptr,
+                                                       SgdHyper h, float gscale, int32_t* step_ptr,
                                                        int update, const uint32_t* skip) {
+  const float lr = sgd_lr(h.lr_dev, h.lr);
   // a latched collective failure (skip != 0): keep the parameters, re-pack them unchanged
   const bool upd = update && !(skip && __hip_atomic_load(const_cast<uint32_t*>(skip), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   for (int p = p0 + blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
     float v = params[p];
     if (upd) {
-      float g = grad[p] * gscale;
-      if (mom) {
-        const float b = mu * mom[p] + g;
-        mom[p] = b;
-        g = b;
-      }
-      v = v - lr * g;
+      const float g = grad[p] * gscale;
+      v = sgd_update(v, g, mom ? mom[p] : 0.f, mom ? mom + p : nullptr, lr, h.momentum, h.weight_decay, h.nesterov);
       params[p] = v;
     }
     Packer<Model, T>::pack(p, v, pack);
@@ -135,9 +132,10 @@ __global__ __launch_bounds__(NW * 64) void reduce_sgd_kernel(const float* __rest
                                                              const float* __restrict__ slab_b, int ldb, int nb,
                                                              int split, int p0, int n, float scale, float* __restrict__ params,
                                                              float* __restrict__ grad, float* __restrict__ mom,
-                                                             T* __restrict__ pack, float lr, float mu,
+                                                             T* __restrict__ pack, SgdHyper h,
                                                              int32_t* step_ptr) {
   __shared__ float part[NW][64];
+  const float lr = sgd_lr(h.lr_dev, h.lr);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int p = p0 + blockIdx.x * 64 + lane;
   // the update's operands first: their latency overlaps the slab loads instead of following the reduction
@@ -162,12 +160,7 @@ __global__ __launch_bounds__(NW * 64) void reduce_sgd_kernel(const float* __rest
     for (int i = 0; i < NW; ++i) g += part[i][lane];
     g *= scale;
     grad[p] = g;
-    if (mom) {
-      const float b = mu * mv + g;
-      mom[p] = b;
-      g = b;
-    }
-    const float v = pv - lr * g;
+    const float v = sgd_update(pv, g, mv, mom ? mom + p : nullptr, lr, h.momentum, h.weight_decay, h.nesterov);
     params[p] = v;
     Packer<Model, T>::pack(p, v, pack);
   }
@@ -187,19 +180,15 @@ template <class Model, typename T>
 __global__ __launch_bounds__(rd_block<Model>()) void reduce_sgd_direct_kernel(const float* __restrict__ slab, int ld, int ns, int p0,
                                                                 int n, float scale, float* __restrict__ params,
                                                                 float* __restrict__ grad, float* __restrict__ mom,
-                                                                T* __restrict__ pack, float lr, float mu,
+                                                                T* __restrict__ pack, SgdHyper h,
                                                                 int32_t* step_ptr) {
+  const float lr = sgd_lr(h.lr_dev, h.lr);
   const int p = p0 + blockIdx.x * rd_block<Model>() + threadIdx.x;
   if (p < n) {
     const float pv = params[p], mv = mom ? mom[p] : 0.f;  // issued with the slab loads
-    float g = slab_sum_direct(slab, ld, ns, p) * scale;
+    const float g = slab_sum_direct(slab, ld, ns, p) * scale;
     grad[p] = g;
-    if (mom) {
-      const float b = mu * mv + g;
-      mom[p] = b;
-      g = b;
-    }
-    const float v = pv - lr * g;
+    const float v = sgd_update(pv, g, mv, mom ? mom + p : nullptr, lr, h.momentum, h.weight_decay, h.nesterov);
     params[p] = v;
     Packer<Model, T>::pack(p, v, pack);
   }
@@ -211,7 +200,7 @@ __global__ __launch_bounds__(rd_block<Model>()) void reduce_sgd_direct_kernel(co
 
 template <class Model, typename T>
 void reduce_sgd_t(const float* sa, int lda, int na, const float* sb, int ldb, int nb, int split, int p0, int n, float scale,
-                  float* params, float* grad, float* mom, void* pack, float lr, float mu, int32_t* step_ptr,
+                  float* params, float* grad, float* mom, void* pack, const SgdHyper& h, int32_t* step_ptr,
                   hipStream_t s) {
   if (n <= p0) return;
   const bool only_b = p0 >= split, only_a = n <= split;
@@ -219,20 +208,20 @@ void reduce_sgd_t(const float* sa, int lda, int na, const float* sb, int ldb, in
     constexpr int RB = rd_block<Model>();
     hipLaunchKernelGGL((reduce_sgd_direct_kernel<Model, T>), dim3((n - p0 + RB - 1) / RB), dim3(RB), 0, s,
                        only_b ? sb : sa, only_b ? ldb : lda, only_b ? nb : na, p0, n, scale, params, grad, mom,
-                       reinterpret_cast<T*>(pack), lr, mu, step_ptr);
+                       reinterpret_cast<T*>(pack), h, step_ptr);
     return;
   }
   const int grid = (n - p0 + 63) / 64;
   hipLaunchKernelGGL((reduce_sgd_kernel<Model, T, RNW>), dim3(grid), dim3(RNW * 64), 0, s, sa, lda, na, sb, ldb, nb, split,
-                     p0, n, scale, params, grad, mom, reinterpret_cast<T*>(pack), lr, mu, step_ptr);
+                     p0, n, scale, params, grad, mom, reinterpret_cast<T*>(pack), h, step_ptr);
 }
 
 template <class Model, typename T>
-void sgd_launch(float* params, const float* grad, float* mom, void* pack, int p0, int n, float lr, float mu,
+void sgd_launch(float* params, const float* grad, float* mom, void* pack, int p0, int n, const SgdHyper& h,
                 float gscale, int32_t* step_ptr, int update, hipStream_t s, const uint32_t* skip = nullptr) {
   const int grid = std::max(1, std::min(1024, (n - p0 + 255) / 256));
   hipLaunchKernelGGL((sgd_pack_kernel<Model, T>), dim3(grid), dim3(256), 0, s, params, grad, mom,
-                     reinterpret_cast<T*>(pack), p0, n, lr, mu, gscale, step_ptr, update, skip);
+                     reinterpret_cast<T*>(pack), p0, n, h, gscale, step_ptr, update, skip);
 }
 
 // Bounded busy wait of `ticks` periods of the 100 MHz wall clock (one lane; tests of the collective
@@ -267,22 +256,22 @@ void launch_reduce(const float* slab, int slab_ld, int nslab, int p0, int p1, fl
 }
 
 void launch_sgd_pack_range(ModelKind m, DType t, float* params, const float* grad, float* mom, void* pack, int p0,
-                           int p1, float lr, float momentum, float gscale, int32_t* step_ptr, hipStream_t s,
+                           int p1, const SgdHyper& h, float gscale, int32_t* step_ptr, hipStream_t s,
                            const uint32_t* skip) {
   if (p1 <= p0) return;
-  float* mb = momentum != 0.f ? mom : nullptr;
+  float* mb = h.momentum != 0.f ? mom : nullptr;
   if (m == ModelKind::MLP) {
-    if (t == DType::F32) sgd_launch<MlpModel, float>(params, grad, mb, pack, p0, p1, lr, momentum, gscale, step_ptr, 1, s, skip);
-    else sgd_launch<MlpModel, bf16>(params, grad, mb, pack, p0, p1, lr, momentum, gscale, step_ptr, 1, s, skip);
+    if (t == DType::F32) sgd_launch<MlpModel, float>(params, grad, mb, pack, p0, p1, h, gscale, step_ptr, 1, s, skip);
+    else sgd_launch<MlpModel, bf16>(params, grad, mb, pack, p0, p1, h, gscale, step_ptr, 1, s, skip);
   } else {
-    if (t == DType::F32) sgd_launch<LenetModel, float>(params, grad, mb, pack, p0, p1, lr, momentum, gscale, step_ptr, 1, s, skip);
-    else sgd_launch<LenetModel, bf16>(params, grad, mb, pack, p0, p1, lr, momentum, gscale, step_ptr, 1, s, skip);
+    if (t == DType::F32) sgd_launch<LenetModel, float>(params, grad, mb, pack, p0, p1, h, gscale, step_ptr, 1, s, skip);
+    else sgd_launch<LenetModel, bf16>(params, grad, mb, pack, p0, p1, h, gscale, step_ptr, 1, s, skip);
   }
 }
 
 void launch_sgd_pack(ModelKind m, DType t, float* params, const float* grad, float* mom, void* pack, int nparam,
-                     float lr, float momentum, float gscale, int32_t* step_ptr, hipStream_t s, const uint32_t* skip) {
-  launch_sgd_pack_range(m, t, params, grad, mom, pack, 0, nparam, lr, momentum, gscale, step_ptr, s, skip);
+                     const SgdHyper& h, float gscale, int32_t* step_ptr, hipStream_t s, const uint32_t* skip) {
+  launch_sgd_pack_range(m, t, params, grad, mom, pack, 0, nparam, h, gscale, step_ptr, s, skip);
 }
 
 void launch_spin(double seconds, hipStream_t s) {
@@ -293,11 +282,11 @@ void launch_spin(double seconds, hipStream_t s) {
 void launch_pack(ModelKind m, DType t, const float* params, void* pack, int nparam, hipStream_t s) {
   float* p = const_cast<float*>(params);
   if (m == ModelKind::MLP) {
-    if (t == DType::F32) sgd_launch<MlpModel, float>(p, nullptr, nullptr, pack, 0, nparam, 0.f, 0.f, 0.f, nullptr, 0, s);
-    else sgd_launch<MlpModel, bf16>(p, nullptr, nullptr, pack, 0, nparam, 0.f, 0.f, 0.f, nullptr, 0, s);
+    if (t == DType::F32) sgd_launch<MlpModel, float>(p, nullptr, nullptr, pack, 0, nparam, SgdHyper{}, 0.f, nullptr, 0, s);
+    else sgd_launch<MlpModel, bf16>(p, nullptr, nullptr, pack, 0, nparam, SgdHyper{}, 0.f, nullptr, 0, s);
   } else {
-    if (t == DType::F32) sgd_launch<LenetModel, float>(p, nullptr, nullptr, pack, 0, nparam, 0.f, 0.f, 0.f, nullptr, 0, s);
-    else sgd_launch<LenetModel, bf16>(p, nullptr, nullptr, pack, 0, nparam, 0.f, 0.f, 0.f, nullptr, 0, s);
+    if (t == DType::F32) sgd_launch<LenetModel, float>(p, nullptr, nullptr, pack, 0, nparam, SgdHyper{}, 0.f, nullptr, 0, s);
+    else sgd_launch<LenetModel, bf16>(p, nullptr, nullptr, pack, 0, nparam, SgdHyper{}, 0.f, nullptr, 0, s);
   }
 }
 
@@ -326,13 +315,13 @@ int model_job_begin(ModelKind m, int job) {
 
 void launch_reduce_sgd(ModelKind m, DType t, const float* slab_a, int lda, int na, const float* slab_b, int ldb,
                        int nb, int split, int p0, int n, float scale, float* params, float* grad, float* mom,
-                       void* pack, float lr, float momentum, int32_t* step_ptr, hipStream_t s) {
-  float* mb = momentum != 0.f ? mom : nullptr;
+                       void* pack, const SgdHyper& h, int32_t* step_ptr, hipStream_t s) {
+  float* mb = h.momentum != 0.f ? mom : nullptr;
   if (m == ModelKind::MLP) {
-    if (t == DType::F32) reduce_sgd_t<MlpModel, float>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, lr, momentum, step_ptr, s);
-    else reduce_sgd_t<MlpModel, bf16>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, lr, momentum, step_ptr, s);
+    if (t == DType::F32) reduce_sgd_t<MlpModel, float>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, h, step_ptr, s);
+    else reduce_sgd_t<MlpModel, bf16>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, h, step_ptr, s);
   } else {
-    if (t == DType::F32) reduce_sgd_t<LenetModel, float>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, lr, momentum, step_ptr, s);
-    else reduce_sgd_t<LenetModel, bf16>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, lr, momentum, step_ptr, s);
+    if (t == DType::F32) reduce_sgd_t<LenetModel, float>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, h, step_ptr, s);
+    else reduce_sgd_t<LenetModel, bf16>(slab_a, lda, na, slab_b, ldb, nb, split, p0, n, scale, params, grad, mb, pack, h, step_ptr, s);
   }
 }

@@ -100,6 +100,7 @@ DEV void wgrad_sgd_tile(const WgArgs<T>& a, int tile) {
     pv[i] = a.sgd.params[p];
     mv[i] = a.sgd.mom ? a.sgd.mom[p] : 0.f;
   }
+  const float lr = sgd_lr(a.sgd.h.lr_dev, a.sgd.h.lr);  // published by this step's head kernel
   f32x4 acc = zero4();
 #pragma unroll
   for (int st = 0; st < FPS; ++st)
@@ -113,14 +114,10 @@ DEV void wgrad_sgd_tile(const WgArgs<T>& a, int tile) {
   for (int i = 0; i < 4; ++i) {
     if (pidx[i] < 0) continue;
     const int p = pidx[i];
-    float g = (0.f + acc[i]) * a.sgd.scale;  // = reduce_sgd over one slab
+    const float g = (0.f + acc[i]) * a.sgd.scale;  // = reduce_sgd over one slab
     a.sgd.grad[p] = g;
-    if (a.sgd.mom) {
-      const float b = a.sgd.momentum * mv[i] + g;
-      a.sgd.mom[p] = b;
-      g = b;
-    }
-    const float nv = pv[i] - a.sgd.lr * g;
+    const float nv = sgd_update(pv[i], g, mv[i], a.sgd.mom ? a.sgd.mom + p : nullptr, lr, a.sgd.h.momentum,
+                                a.sgd.h.weight_decay, a.sgd.h.nesterov);
     a.sgd.params[p] = nv;
     Packer<Model, T>::pack(p, nv, reinterpret_cast<T*>(a.sgd.pack));
   }

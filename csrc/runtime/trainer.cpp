@@ -106,6 +106,8 @@ Trainer::Trainer(int model, int dtype, int batch, int ld_b, int fc_splits, const
   for (auto& e : events_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_CHECK(hipMalloc(&zero_counter_, 2 * sizeof(int32_t)));
   HIP_CHECK(hipMemset(zero_counter_, 0, 2 * sizeof(int32_t)));
+  HIP_CHECK(hipMalloc(&lr_sched_, sizeof(LrSched)));
+  HIP_CHECK(hipMemset(lr_sched_, 0, sizeof(LrSched)));
 }
 
 Trainer::~Trainer() { destroy(); }
@@ -122,8 +124,11 @@ void Trainer::destroy() {
   if (comm_stream_) hipStreamDestroy(comm_stream_);
   if (aux_stream_) hipStreamDestroy(aux_stream_);
   if (zero_counter_) hipFree(zero_counter_);
+  if (lr_sched_) hipFree(lr_sched_);
   comm_stream_ = aux_stream_ = last_stream_ = nullptr;
   zero_counter_ = nullptr;
+  lr_sched_ = nullptr;
+  lr_n_ = 0;
   comm_.reset();
   oneshot_.reset();
   ov_fc_.reset();
@@ -147,6 +152,31 @@ void Trainer::release() {
   ov_fc_.reset();
   ov_conv_.reset();
   if (plan_ == Plan::OVERLAP) plan_ = Plan::JOIN;
+}
+
+void Trainer::set_optimizer(float lr, float momentum, float weight_decay, bool nesterov) {
+  if (!(weight_decay >= 0.f)) throw std::invalid_argument("Invalid weight_decay value: " + std::to_string(weight_decay));
+  if (nesterov && momentum == 0.f) throw std::invalid_argument("Nesterov momentum requires a momentum (and zero dampening)");
+  lr_ = lr;
+  momentum_ = momentum;
+  weight_decay_ = weight_decay;
+  nesterov_ = nesterov;
+  invalidate();  // every captured update kernel holds them as arguments
+}
+
+void Trainer::set_lr_table(uintptr_t table, int n, uintptr_t cell) {
+  const float* t = n > 0 && table && cell ? ptr<const float>(table) : nullptr;
+  const int nn = t ? n : 0;
+  float* c = t ? ptr<float>(cell) : nullptr;
+  // the graphs captured the three values, not the table's contents: new rates at the same address keep them
+  if (t == lr_table_ && nn == lr_n_ && c == lr_cell_) return;
+  invalidate();
+  sync_own_streams();  // eager steps still in flight read the descriptor
+  lr_table_ = t;
+  lr_n_ = nn;
+  lr_cell_ = c;
+  const LrSched d{t, c, nn};
+  HIP_CHECK(hipMemcpy(lr_sched_, &d, sizeof(d), hipMemcpyHostToDevice));
 }
 
 int Trainer::fc_splits_for(int B) const {
@@ -370,6 +400,7 @@ HeadBuffers Trainer::head_buffers(float* metrics) const {
   hb.drop_p = drop_p_;
   hb.xcd = xcd_map();
   hb.ablate = ablation_mask("MNIST_AMD_HEAD_ABLATE");
+  if (lr_n_ > 0) hb.lr_sched = lr_sched_;  // a schedule: the training head publishes the step's rate (launch.h)
   return hb;
 }
 
@@ -442,7 +473,7 @@ void Trainer::reduce_grads(int B, uintptr_t stream) {
 
 void Trainer::optimizer_step(float gscale, uintptr_t stream) {
   launch_sgd_pack(model_, dtype_, ptr<float>(p_.params), ptr<const float>(p_.grad), ptr<float>(p_.mom),
-                  ptr<void>(p_.pack), nparam_, lr_, momentum_, gscale, ptr<int32_t>(p_.step), S(stream));
+                  ptr<void>(p_.pack), nparam_, hyper(), gscale, ptr<int32_t>(p_.step), S(stream));
   post_launch(S(stream));
 }
 
@@ -550,7 +581,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
     // branch; bitwise equal to wgrad -> reduce_sgd)
     int splits = 1;
     if (fc_splits_ == 1 && fuse_wgrad_sgd_) {
-      const SgdFuse f{scale, lr_, momentum_, ptr<float>(p_.params), ptr<float>(p_.grad),
+      const SgdFuse f{scale, hyper(), ptr<float>(p_.params), ptr<float>(p_.grad),
                       momentum_ != 0.f ? ptr<float>(p_.mom) : nullptr, ptr<void>(p_.pack), nullptr};
       launch_head_wgrad(model_, dtype_, hb, B, 1, ptr<float>(p_.slab_fc), fc_ld_, aux_stream_, hrows, &f);
       post_launch(aux_stream_);
@@ -559,7 +590,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
       post_launch(aux_stream_);
       launch_reduce_sgd(model_, dtype_, ptr<const float>(p_.slab_conv), cp, nslab, ptr<const float>(p_.slab_fc),
                         fc_ld_, splits, cp, cp, nparam_, scale, ptr<float>(p_.params), ptr<float>(p_.grad),
-                        ptr<float>(p_.mom), ptr<void>(p_.pack), lr_, momentum_, nullptr, aux_stream_);
+                        ptr<float>(p_.mom), ptr<void>(p_.pack), hyper(), nullptr, aux_stream_);
       post_launch(aux_stream_);
     }
     HIP_CHECK(hipEventRecord(events_[5], aux_stream_));
@@ -569,7 +600,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
     else HIP_CHECK(hipStreamWaitEvent(s, events_[5], 0));
     launch_reduce_sgd(model_, dtype_, ptr<const float>(p_.slab_conv), cp, nslab, ptr<const float>(p_.slab_fc),
                       fc_ld_, splits, cp, 0, cp, scale, ptr<float>(p_.params), ptr<float>(p_.grad),
-                      ptr<float>(p_.mom), ptr<void>(p_.pack), lr_, momentum_, ptr<int32_t>(p_.step), s);
+                      ptr<float>(p_.mom), ptr<void>(p_.pack), hyper(), ptr<int32_t>(p_.step), s);
     post_launch(s);
     return;
   }
@@ -580,7 +611,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
   }
   if (model_ == ModelKind::MLP && fc_splits_ == 1 && fuse_wgrad_sgd_) {
     // one GPU, one batch split: the SGD update is the wgrad kernel's epilogue (no reduce_sgd kernel)
-    const SgdFuse f{scale, lr_, momentum_, ptr<float>(p_.params), ptr<float>(p_.grad),
+    const SgdFuse f{scale, hyper(), ptr<float>(p_.params), ptr<float>(p_.grad),
                     momentum_ != 0.f ? ptr<float>(p_.mom) : nullptr,  // as launch_reduce_sgd
                     ptr<void>(p_.pack), ptr<int32_t>(p_.step)};
     launch_head_wgrad(model_, dtype_, hb, B, 1, ptr<float>(p_.slab_fc), fc_ld_, s, hrows, &f);
@@ -591,7 +622,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
     // serial single-GPU schedule, one FC batch split (small batches): the FC update is the wgrad kernel's
     // epilogue (it touches only FC parameters / operand images, which conv_bwd does not read), and the closing
     // reduce + SGD covers the conv parameters only (bitwise equal to wgrad -> reduce_sgd over all of them)
-    const SgdFuse f{scale, lr_, momentum_, ptr<float>(p_.params), ptr<float>(p_.grad),
+    const SgdFuse f{scale, hyper(), ptr<float>(p_.params), ptr<float>(p_.grad),
                     momentum_ != 0.f ? ptr<float>(p_.mom) : nullptr, ptr<void>(p_.pack), nullptr};
     // ... as extra workgroups of the conv_bwd launch (one kernel instead of two; the FC wgrad + update as its own
     // kernel before conv_bwd measured 31.0 vs 25.8 us per B = 128 step, profiles/r4_session2/NOTES.md)
@@ -599,7 +630,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
     post_launch(s);
     launch_reduce_sgd(model_, dtype_, ptr<const float>(p_.slab_conv), cp, nslab, ptr<const float>(p_.slab_fc),
                       fc_ld_, 1, cp, 0, cp, scale, ptr<float>(p_.params), ptr<float>(p_.grad), ptr<float>(p_.mom),
-                      ptr<void>(p_.pack), lr_, momentum_, ptr<int32_t>(p_.step), s);
+                      ptr<void>(p_.pack), hyper(), ptr<int32_t>(p_.step), s);
     post_launch(s);
     return;
   }
@@ -613,7 +644,7 @@ void Trainer::launch_step(int B, hipStream_t s, bool defer_join) {
   // no communicator: ONE fused reduce + SGD + pack kernel (2 boundaries fewer than reduce -> sgd)
   launch_reduce_sgd(model_, dtype_, ptr<const float>(p_.slab_conv), cp, nslab, ptr<const float>(p_.slab_fc),
                     fc_ld_, splits, cp, 0, nparam_, scale, ptr<float>(p_.params), ptr<float>(p_.grad),
-                    ptr<float>(p_.mom), ptr<void>(p_.pack), lr_, momentum_, ptr<int32_t>(p_.step), s);
+                    ptr<float>(p_.mom), ptr<void>(p_.pack), hyper(), ptr<int32_t>(p_.step), s);
   post_launch(s);
 }
 
@@ -625,7 +656,7 @@ void Trainer::comm_phase(int g, hipEvent_t ready, bool bump) {
   all_reduce(buckets_, g, comm_stream_);
   const Group gr = groups().at(g);
   launch_sgd_pack_range(model_, dtype_, ptr<float>(p_.params), ptr<const float>(p_.grad), ptr<float>(p_.mom),
-                        ptr<void>(p_.pack), gr.p0, gr.p1, lr_, momentum_, 1.0f / float(world_),
+                        ptr<void>(p_.pack), gr.p0, gr.p1, hyper(), 1.0f / float(world_),
                         bump ? ptr<int32_t>(p_.step) : nullptr, comm_stream_, dp_skip());
   post_launch(comm_stream_);
 }
@@ -644,8 +675,8 @@ void Trainer::launch_mlp_comm_tail(int B, hipStream_t s, const HeadBuffers& hb, 
     launch_reduce(slab, fc_ld_, splits, 0, nparam_, scale, g, s);
     post_launch(s);
     all_reduce(coalesced_buckets(), -1, s);
-    launch_sgd_pack(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), nparam_, lr_,
-                    momentum_, 1.0f / float(world_), ptr<int32_t>(p_.step), s, dp_skip());
+    launch_sgd_pack(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), nparam_, hyper(),
+                    1.0f / float(world_), ptr<int32_t>(p_.step), s, dp_skip());
     post_launch(s);
     return;
   }
@@ -680,8 +711,8 @@ void Trainer::launch_lenet_comm_tail(int B, int nslab, int splits, hipStream_t s
     post_launch(s);
     HIP_CHECK(hipStreamWaitEvent(s, events_[5], 0));
     all_reduce(coalesced_buckets(), -1, s);
-    launch_sgd_pack(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), nparam_, lr_,
-                    momentum_, gs, ptr<int32_t>(p_.step), s, dp_skip());
+    launch_sgd_pack(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), nparam_, hyper(),
+                    gs, ptr<int32_t>(p_.step), s, dp_skip());
     post_launch(s);
     return;
   }
@@ -743,14 +774,14 @@ void Trainer::launch_lenet_overlap(int B, int nslab, hipStream_t s, const HeadBu
   post_launch(aux_stream_);
   ov_fc_->all_reduce_sum_f32(g + cp, size_t(nparam_ - cp), aux_stream_);
   launch_sgd_pack_range(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), cp, nparam_,
-                        lr_, momentum_, gs, nullptr, aux_stream_, ov_fc_->err_word());
+                        hyper(), gs, nullptr, aux_stream_, ov_fc_->err_word());
   post_launch(aux_stream_);
   HIP_CHECK(hipEventRecord(events_[5], aux_stream_));
   launch_reduce(ptr<const float>(p_.slab_conv), cp, nslab, 0, cp, scale, g, s);
   post_launch(s);
   ov_conv_->all_reduce_sum_f32(g, size_t(cp), s);
-  launch_sgd_pack_range(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), 0, cp, lr_,
-                        momentum_, gs, ptr<int32_t>(p_.step), s, ov_conv_->err_word());
+  launch_sgd_pack_range(model_, dtype_, ptr<float>(p_.params), g, ptr<float>(p_.mom), ptr<void>(p_.pack), 0, cp, hyper(),
+                        gs, ptr<int32_t>(p_.step), s, ov_conv_->err_word());
   post_launch(s);
 }
 
@@ -785,6 +816,7 @@ void Trainer::eval_batch(uintptr_t images, uintptr_t labels, uintptr_t idx, int 
   br.batch_stride = 0;
   br.B = B;
   HeadBuffers hb = head_buffers(ptr<float>(metrics));
+  hb.lr_sched = nullptr;  // forward only, zero counter: the schedule's cell is not touched
   if (model_ == ModelKind::LENET) {
     launch_lenet_conv_fwd(dtype_, false, br, conv_buffers(), s);
     post_launch(s);

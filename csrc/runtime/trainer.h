@@ -78,7 +78,16 @@ class Trainer {
   void set_comm_enabled(bool on) { comm_enabled_ = on; }
   bool comm_enabled() const { return comm_enabled_; }
   void set_world(int w) { world_ = w; invalidate(); }
-  void set_optimizer(float lr, float momentum) { lr_ = lr; momentum_ = momentum; invalidate(); }
+  // torch.optim.SGD(lr, momentum, dampening=0, weight_decay, nesterov); kernel arguments of every captured update, so a
+  // change drops the graphs.  Throws std::invalid_argument as torch raises ValueError (weight_decay < 0; nesterov
+  // without momentum).
+  void set_optimizer(float lr, float momentum, float weight_decay = 0.f, bool nesterov = false);
+  // Learning-rate schedule: a device table of n float32 rates indexed by the global step (step_ctr[1]; steps >= n use
+  // the last entry) and a one-float device cell.  Every training head publishes the step's rate into the cell and
+  // the update kernels read it instead of lr, so ONE captured graph serves the whole schedule.  Zero / null clears
+  // it.  Graphs are dropped when an address or n changes; new contents at the same addresses keep them.
+  void set_lr_table(uintptr_t table, int n, uintptr_t cell);
+  bool has_lr_table() const { return lr_n_ > 0; }
   void set_dropout(float p, uint32_t seed) { drop_p_ = p; seed_ = seed; invalidate(); }
   // validated (contiguous groups in ready order on unit boundaries); graphs are cached per bucket plan
   void set_buckets(const std::vector<Bucket>& b);
@@ -216,6 +225,14 @@ class Trainer {
   int fc_ld_ = 0;  // FC slab row stride: nparam rounded up to 4 floats (16-byte aligned rows for the wide slab stores)
   TrainerPtrs p_;
   float lr_ = 0.01f, momentum_ = 0.f, drop_p_ = 0.2f;
+  float weight_decay_ = 0.f;
+  bool nesterov_ = false;
+  const float* lr_table_ = nullptr;  // device schedule (set_lr_table) or null
+  float* lr_cell_ = nullptr;
+  int lr_n_ = 0;
+  LrSched* lr_sched_ = nullptr;  // device copy of {lr_table_, lr_cell_, lr_n_}: what the head kernels read
+  // the update kernels' hyper-parameters: the rate from the cell when a schedule is installed
+  SgdHyper hyper() const { return SgdHyper{lr_, momentum_, weight_decay_, nesterov_ ? 1 : 0, lr_n_ > 0 ? lr_cell_ : nullptr}; }
   uint32_t seed_ = 1234;
   int world_ = 1;
   Plan plan_ = Plan::JOIN;

@@ -12,7 +12,7 @@ Reference behaviour reproduced here:
 
 Additive flags (survey §5.6): --model, --dtype, --momentum, --lr, --synthetic,
 --bucket_cap_kb, --profile, --seed, --no_save, --comm, --no_graph, --plan, --allreduce, --tqdm, --progress_every,
---resume, --io_mode.
+--resume, --io_mode, --weight_decay, --nesterov, --lr_schedule, --warmup_steps, --lr_min, --lr_step_size, --lr_gamma.
 """
 from __future__ import annotations
 
@@ -24,6 +24,7 @@ from typing import List, Optional
 WIREUP_METHODS = ["nccl-slurm", "nccl-openmpi", "nccl-mpich", "gloo"]
 WIREUP_METHODS_PNETCDF = WIREUP_METHODS + ["mpich"]
 MODELS = ["mlp", "lenet5"]
+LR_SCHEDULES = ["constant", "step", "cosine", "linear"]
 DTYPES = ["fp32", "bf16"]
 
 
@@ -63,6 +64,13 @@ class TrainConfig:
     io_mode: str = "bulk"       # netCDF: "bulk" (one pread per variable) | "per_sample" (reference __getitem__
                                 # reads, whole epoch first) | "interleaved" (each batch read before its step)
     resume: Optional[str] = None  # params + momentum + epoch file: loaded if present, rewritten each epoch
+    weight_decay: float = 0.0   # torch.optim.SGD weight_decay (every parameter, biases included)
+    nesterov: bool = False      # torch.optim.SGD nesterov (needs --momentum)
+    lr_schedule: Optional[str] = None  # per-step learning rate (optim/schedule.py): constant | step | cosine | linear
+    warmup_steps: int = 0       # linear warm-up to --lr over the first steps of the schedule
+    lr_min: float = 0.0         # cosine / linear: the rate the schedule ends at
+    lr_step_size: Optional[int] = None  # step: steps between decays
+    lr_gamma: float = 0.1       # step: decay factor
 
     def to_nested(self) -> dict:
         """Nested dict in the reference layout (mnist_cpu_mp.py:223-241)."""
@@ -121,12 +129,21 @@ def _add_extra_flags(p: argparse.ArgumentParser, defaults: TrainConfig) -> None:
              "per_sample reads the epoch first, interleaved reads each batch beside the training steps")
     add("--resume", type=str, default=None,
         help="resume file (params + momentum + epoch): loaded when it exists, rewritten after every epoch")
+    add("--weight_decay", type=float, default=None, help="SGD weight decay, torch.optim.SGD semantics (default 0)")
+    add("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum)")
+    add("--lr_schedule", type=str, default=None, choices=LR_SCHEDULES,
+        help="per-step learning-rate schedule over the run's steps, from --lr (default: none, the constant --lr)")
+    add("--warmup_steps", type=int, default=None, help="--lr_schedule: linear warm-up steps up to --lr")
+    add("--lr_min", type=float, default=None, help="--lr_schedule cosine / linear: final learning rate")
+    add("--lr_step_size", type=int, default=None, help="--lr_schedule step: steps between decays")
+    add("--lr_gamma", type=float, default=None, help="--lr_schedule step: decay factor (default 0.1)")
 
 
 def _apply_extra(cfg: TrainConfig, a: argparse.Namespace) -> None:
     for name in ("model", "dtype", "lr", "momentum", "dropout", "seed", "init_seed", "data_format",
                  "device", "bucket_cap_kb", "comm", "save_path", "metrics_jsonl", "plan", "resume", "progress_every",
-                 "io_mode", "allreduce"):
+                 "io_mode", "allreduce", "weight_decay", "lr_schedule", "warmup_steps", "lr_min", "lr_step_size",
+                 "lr_gamma"):
         v = getattr(a, name, None)
         if v is not None:
             setattr(cfg, name, v)
@@ -142,6 +159,8 @@ def _apply_extra(cfg: TrainConfig, a: argparse.Namespace) -> None:
         cfg.disable_tqdm = False
     if getattr(a, "shard_eval", False):
         cfg.shard_eval = True
+    if getattr(a, "nesterov", False):
+        cfg.nesterov = True
 
 
 def mp_parser(pnetcdf: bool = False) -> argparse.ArgumentParser:

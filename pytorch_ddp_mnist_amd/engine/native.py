@@ -32,6 +32,7 @@ import torch
 
 from ..models import MODEL_IDS, build_model, flatten_state, unflatten_state
 from ..ops.native import require_gpu
+from ..optim.schedule import check_sgd_options, validate_lr_table
 from ..parallel.comm import comm_timeout  # noqa: F401  (re-exported: watchdog deadline)
 
 PLANS = {"join": 0, "split": 1, "overlap": 2}
@@ -178,7 +179,11 @@ class NativeTrainer:
     def __init__(self, model: str, dtype: str, batch: int, images: torch.Tensor, labels: torch.Tensor,
                  device: Optional[torch.device] = None, lr: float = 0.01, momentum: float = 0.0,
                  dropout: float = 0.2, seed: int = 1234, fc_splits: Optional[int] = None,
-                 init: Optional[torch.nn.Module] = None, max_indices: Optional[int] = None):
+                 init: Optional[torch.nn.Module] = None, max_indices: Optional[int] = None,
+                 weight_decay: float = 0.0, nesterov: bool = False, lr_schedule=None):
+        """``lr`` / ``momentum`` / ``weight_decay`` / ``nesterov``: torch.optim.SGD's (dampening 0), applied after
+        the DDP average.  ``lr_schedule``: per-step rates (see :meth:`set_lr_schedule`)."""
+        check_sgd_options(float(momentum), float(weight_decay), bool(nesterov))
         C = require_gpu()
         self.C = C
         self.model_name = model
@@ -262,7 +267,14 @@ class NativeTrainer:
         P.stamps = ptr(self.stamps)
         self._ptrs = P
         self.rt = C.Trainer(mid, did, self.batch, self.ld_b, fc_splits, P)
-        self.rt.set_optimizer(float(lr), float(momentum))
+        self.lr, self.momentum = float(lr), float(momentum)
+        self.weight_decay, self.nesterov = float(weight_decay), bool(nesterov)
+        if self.weight_decay != 0.0 or self.nesterov:
+            self.rt.set_optimizer(self.lr, self.momentum, self.weight_decay, self.nesterov)
+        else:  # (the two-argument form: also what an earlier build of the extension takes, scripts/build_ab.sh)
+            self.rt.set_optimizer(self.lr, self.momentum)
+        self.lr_table = None   # device float32 [T]: the installed schedule (set_lr_schedule)
+        self.lr_now = None     # device float32 [1]: the rate the head kernel published for the current step
         self.rt.set_dropout(float(dropout), int(seed) & 0xFFFFFFFF)
         self._base_buckets = [(b.p0, b.p1, b.phase) for b in self.rt.buckets()]  # the native default (2 groups)
         _LIVE_TRAINERS.add(self)
@@ -278,6 +290,61 @@ class NativeTrainer:
             self.load_module(init)
         else:
             self.load_module(self.module_template)
+        if lr_schedule is not None:
+            self.set_lr_schedule(lr_schedule)
+
+    # ------------------------------------------------------------------ optimizer
+    def set_lr_schedule(self, table) -> None:
+        """Install per-step learning rates: ``table[t]`` (a sequence or 1-D tensor; non-empty, finite, non-negative)
+        is the rate of global step ``t`` (``step_ctr[1]``, which ``--resume`` restores), steps at or beyond its length
+        use the last entry; ``None`` goes back to the constant ``lr``.
+
+        The table lives on the device; every training step's head kernel publishes the step's rate into a one-float
+        cell and the update kernels read that cell, so the captured step graphs serve the whole schedule.  A table
+        of the installed length is copied over the installed one (the graphs stay); another length, installing or
+        clearing re-captures."""
+        if table is None:
+            if self.lr_table is not None:
+                self.synchronize()
+                self.rt.set_lr_table(0, 0, 0)
+                self.lr_table = None
+            return
+        host = torch.from_numpy(validate_lr_table(table))
+        if self.lr_now is None:
+            self.lr_now = _alloc((1,), torch.float32, self.device, self._guards)
+        with torch.cuda.stream(self.stream):  # ordered behind the steps already queued on the trainer stream
+            if self.lr_table is None or self.lr_table.numel() != host.numel():
+                old = self.lr_table
+                self.lr_table = _alloc((host.numel(),), torch.float32, self.device, self._guards)
+                self.lr_table.copy_(host)
+                self.rt.set_lr_table(self.lr_table.data_ptr(), host.numel(), self.lr_now.data_ptr())  # drains the steps
+                del old
+            else:
+                self.lr_table.copy_(host)
+            # until the next head publishes: the rate of the step about to run
+            t = self.step_ctr[1].long().clamp(0, host.numel() - 1)
+            self.lr_now.copy_(self.lr_table[t].view(1))
+
+    def current_lr(self) -> float:
+        """The learning rate of the step that ran last (the cell its head kernel published), ``lr`` without a
+        schedule."""
+        if self.lr_table is None:
+            return self.lr
+        self.synchronize()
+        return float(self.lr_now.item())
+
+    def get_state(self):
+        """(parameters, momentum, global step) on the host: what ``--resume`` saves."""
+        self.synchronize()
+        return (self.params.detach().cpu().clone(), self.mom.detach().cpu().clone(), int(self.step_ctr[1].item()))
+
+    def set_state(self, params: torch.Tensor, mom, global_step: int = 0) -> None:
+        self.load_flat(params)
+        with torch.cuda.stream(self.stream):  # ordered before the next step on the trainer stream
+            if mom is not None:
+                self.mom.copy_(mom.to(self.mom.device), non_blocking=True)
+            self.step_ctr[1].fill_(int(global_step))  # dropout stream and lr schedule continue, not replayed
+        self.synchronize()
 
     # ------------------------------------------------------------------ parameters
     def _sync_in(self):

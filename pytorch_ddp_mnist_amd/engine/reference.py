@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from ..data.datasets import normalize_batch
 from ..data.sampler import batch_slices
 from ..models import build_model
+from ..optim.schedule import lr_at, validate_lr_table
 from ..parallel.ddp import GlooReducer, model_phases, plan_buckets
 from ..utils.fault import FaultInjector
 
@@ -50,7 +51,10 @@ class TorchCPUEngine:
 
     def __init__(self, model: str, batch: int, lr: float, momentum: float, dropout: float,
                  xtr: np.ndarray, ytr: np.ndarray, xte: np.ndarray, yte: np.ndarray, world: int = 1,
-                 bucket_cap_kb: Optional[int] = None, init: Optional[torch.nn.Module] = None):
+                 bucket_cap_kb: Optional[int] = None, init: Optional[torch.nn.Module] = None,
+                 weight_decay: float = 0.0, nesterov: bool = False, lr_schedule=None):
+        """``weight_decay`` / ``nesterov`` go to torch.optim.SGD; ``lr_schedule`` (per-step rates, optim/schedule.py)
+        sets the param-group ``lr`` from ``global_step`` before each step -- the native trainer's recurrence."""
         self.model_name, self.batch = model, batch
         # share the host's cores between co-located ranks instead of oversubscribing them
         local = int(os.environ.get("LOCAL_WORLD_SIZE", world if world > 1 else 1))
@@ -63,7 +67,9 @@ class TorchCPUEngine:
         self.y = torch.from_numpy(ytr.astype(np.int64))
         self.xt = normalize_batch(torch.from_numpy(np.ascontiguousarray(xte))).reshape(shape)
         self.yt = torch.from_numpy(yte.astype(np.int64))
-        self.opt = torch.optim.SGD(self.module.parameters(), lr=lr, momentum=momentum)
+        self.opt = torch.optim.SGD(self.module.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                   nesterov=nesterov)
+        self.lr_table = None if lr_schedule is None else validate_lr_table(lr_schedule)
         cap = None if bucket_cap_kb is None else bucket_cap_kb * 1024
         self.reducer = GlooReducer(self.module, world, plan_buckets(model_phases(model), cap))
         self.crit = F.nll_loss if model == "lenet5" else F.cross_entropy
@@ -96,6 +102,9 @@ class TorchCPUEngine:
             idx = indices[s:s + b]
             x, y = self.x[idx], self.y[idx]
             self.fault.tick()  # before the step, as NativeEngine._step: FAIL_AT_STEP=k -> k completed steps
+            if self.lr_table is not None:
+                for g in self.opt.param_groups:
+                    g["lr"] = lr_at(self.lr_table, self.global_step)
             self.opt.zero_grad()
             out = self.module(x)
             loss = self.crit(out, y)
@@ -162,6 +171,12 @@ class TorchCPUEngine:
                 if mom is not None and self.opt.defaults.get("momentum", 0) != 0:
                     self.opt.state[p]["momentum_buffer"] = mom[off:off + n].view_as(p).clone()
                 off += n
+
+    def set_lr_schedule(self, table) -> None:
+        self.lr_table = None if table is None else validate_lr_table(table)
+
+    def current_lr(self) -> float:
+        return float(self.opt.param_groups[0]["lr"])
 
     def finish(self) -> None:
         pass

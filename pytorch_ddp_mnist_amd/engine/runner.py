@@ -18,8 +18,9 @@ from ..config import TrainConfig
 from ..data.datasets import find_netcdf, load_arrays, synthesize_netcdf
 from ..data.device_loader import upload_netcdf
 from ..data.per_sample import InterleavedLoader, PerSampleReader
-from ..data.sampler import epoch_indices
+from ..data.sampler import epoch_indices, num_samples
 from ..models import build_model
+from ..optim.schedule import build_lr_table, check_sgd_options
 from ..parallel.comm import DistContext, init_distributed
 from ..parallel.ddp import model_phases, plan_buckets
 from ..utils.checkpoint import load_resume, save_model, save_resume
@@ -48,7 +49,8 @@ class NativeEngine:
         self.cfg, self.ctx = cfg, ctx
         self.tr = NativeTrainer(cfg.model, cfg.dtype, cfg.batch_size, images, labels, device=dev, lr=cfg.lr,
                                 momentum=cfg.momentum, dropout=cfg.dropout if cfg.model == "mlp" else 0.0,
-                                seed=cfg.seed * 7919 + ctx.rank, init=init)
+                                seed=cfg.seed * 7919 + ctx.rank, init=init, weight_decay=cfg.weight_decay,
+                                nesterov=cfg.nesterov)
         cap = None if cfg.bucket_cap_kb is None else cfg.bucket_cap_kb * 1024
         self.tr.set_buckets(plan_buckets(model_phases(cfg.model), cap))
         self.torch_comm = ctx.world > 1 and ctx.rccl is None
@@ -121,17 +123,16 @@ class NativeEngine:
         self._load_rows(self.test_images, self.test_labels, x, y)
 
     def get_state(self):
-        self.tr.synchronize()
-        return (self.tr.params.detach().cpu().clone(), self.tr.mom.detach().cpu().clone(),
-                int(self.tr.step_ctr[1].item()))
+        return self.tr.get_state()
 
     def set_state(self, params: torch.Tensor, mom, global_step: int = 0) -> None:
-        self.tr.load_flat(params)
-        with torch.cuda.stream(self.tr.stream):  # ordered before the next step on the trainer stream
-            if mom is not None:
-                self.tr.mom.copy_(mom.to(self.tr.mom.device), non_blocking=True)
-            self.tr.step_ctr[1].fill_(int(global_step))  # dropout stream continues, not replayed
-        self.tr.synchronize()
+        self.tr.set_state(params, mom, global_step)
+
+    def set_lr_schedule(self, table) -> None:
+        self.tr.set_lr_schedule(table)
+
+    def current_lr(self) -> float:
+        return self.tr.current_lr()
 
     def _step(self, b: int) -> None:
         self.fault.tick()
@@ -266,7 +267,25 @@ def make_engine(cfg: TrainConfig, ctx: DistContext, xtr, ytr, xte, yte):
     if ctx.device.type == "cuda":
         return NativeEngine(cfg, ctx, xtr, ytr, xte, yte, init)
     return TorchCPUEngine(cfg.model, cfg.batch_size, cfg.lr, cfg.momentum, cfg.dropout, xtr, ytr, xte, yte,
-                          world=ctx.world, bucket_cap_kb=cfg.bucket_cap_kb, init=init)
+                          world=ctx.world, bucket_cap_kb=cfg.bucket_cap_kb, init=init, weight_decay=cfg.weight_decay,
+                          nesterov=cfg.nesterov)
+
+
+def optimizer_options(cfg: TrainConfig) -> dict:
+    """What the resume file records of the optimizer: a resumed run with other options follows another recurrence."""
+    return {"lr": float(cfg.lr), "momentum": float(cfg.momentum), "weight_decay": float(cfg.weight_decay),
+            "nesterov": bool(cfg.nesterov), "lr_schedule": cfg.lr_schedule or "", "warmup_steps": int(cfg.warmup_steps),
+            "lr_min": float(cfg.lr_min), "lr_step_size": int(cfg.lr_step_size or 0), "lr_gamma": float(cfg.lr_gamma)}
+
+
+def schedule_table(cfg: TrainConfig, n_train: int, world: int):
+    """The run's learning-rate table (None without --lr_schedule): n_epochs x this rank's steps per epoch, the
+    partial last step included; indexed by the global step, which --resume restores."""
+    if not cfg.lr_schedule:
+        return None
+    per_epoch = -(-num_samples(n_train, world) // int(cfg.batch_size))
+    return build_lr_table(cfg.lr_schedule, cfg.lr, max(1, cfg.n_epochs * per_epoch), cfg.warmup_steps, cfg.lr_min,
+                          cfg.lr_step_size, cfg.lr_gamma)
 
 
 def _data_format(cfg: TrainConfig, entry: str) -> str:
@@ -279,6 +298,7 @@ def run(cfg: TrainConfig, entry: str = "ddp_tutorial_cpu", show_banner: bool = F
         ctx: Optional[DistContext] = None) -> dict:
     if cfg.profile:
         enable_roctx(True)
+    check_sgd_options(cfg.momentum, cfg.weight_decay, cfg.nesterov)
     own_ctx = ctx is None
     if ctx is None:
         world_env = int(os.environ.get("WORLD_SIZE", "1"))
@@ -323,6 +343,9 @@ def run(cfg: TrainConfig, entry: str = "ddp_tutorial_cpu", show_banner: bool = F
         print("=> Dataset created, image nc file is : {}".format(os.path.join(root, "mnist_train_images.nc")))
     n_gpus = torch.cuda.device_count() if ctx.device.type == "cuda" else 0
     engine = make_engine(cfg, ctx, xtr, ytr, xte, yte)
+    table = schedule_table(cfg, len(ytr), ctx.world)
+    if table is not None:
+        engine.set_lr_schedule(table)
     if show_banner:
         banner(ctx.rank, ctx.world, n_gpus, ctx.device, src, cfg.num_workers, cfg.n_epochs, cfg.parallel,
                cfg.model, cfg.dtype if ctx.device.type == "cuda" else "fp32", engine.name)
@@ -336,6 +359,11 @@ def run(cfg: TrainConfig, entry: str = "ddp_tutorial_cpu", show_banner: bool = F
             raise ValueError(f"resume file {cfg.resume} holds a {st.get('model')} model, not {cfg.model}")
         engine.set_state(st["params"], st.get("momentum"), int(st.get("global_step", 0)))
         start = int(st["epoch"]) + 1
+        saved_opt = st.get("optimizer")
+        if ctx.rank == 0 and saved_opt is not None and dict(saved_opt) != optimizer_options(cfg):
+            diff = {k: (saved_opt.get(k), v) for k, v in optimizer_options(cfg).items() if saved_opt.get(k) != v}
+            print(f"[rank0] WARNING: {cfg.resume} was written with other optimizer options (saved, now): {diff}",
+                  flush=True)
         if ctx.rank == 0:
             print(f"=> resumed from {cfg.resume} after epoch {st['epoch']}", flush=True)
     timer = PhaseTimer(sync=engine.finish)
@@ -398,6 +426,8 @@ def run(cfg: TrainConfig, entry: str = "ddp_tutorial_cpu", show_banner: bool = F
             rec[f"io_{k}_MBps"], rec[f"io_{k}_samples_per_s"] = st.mb_per_s, st.samples_per_s
             if ctx.rank == 0:
                 print("[rank0] per-sample netCDF " + st.line(k), flush=True)
+        if table is not None:
+            rec["lr"] = engine.current_lr()  # the rate of the epoch's last step
         history.append(rec)
         if ctx.rank == 0:
             print(f"[rank0] epoch={i} global_train_loss={rec['train_loss_mean']:.4f} train_acc={rec['train_acc']:.4f} "
@@ -409,7 +439,8 @@ def run(cfg: TrainConfig, entry: str = "ddp_tutorial_cpu", show_banner: bool = F
         if cfg.resume:
             params, mom, gstep = engine.get_state()  # every rank holds the same replica
             if ctx.rank == 0:
-                save_resume(cfg.resume, params, mom, i, cfg.model, cfg.dtype, global_step=gstep)
+                save_resume(cfg.resume, params, mom, i, cfg.model, cfg.dtype, global_step=gstep,
+                            optimizer=optimizer_options(cfg))
     engine.finish()
     if ctx.world > 1 and _uses_oneshot(engine):
         engine.tr.agree_oneshot(ctx.all_reduce_max)  # every rank raises if any rank latched a one-shot failure

@@ -28,11 +28,14 @@ def load_model(path: str = "model.pt") -> Dict[str, torch.Tensor]:
 
 
 def save_resume(path: str, params: torch.Tensor, momentum: Optional[torch.Tensor], epoch: int,
-                model: str, dtype: str, global_step: int = 0) -> str:
-    """``global_step`` seeds the native dropout stream: restoring it keeps the masks of a resumed run
-    from replaying those of the first epochs."""
+                model: str, dtype: str, global_step: int = 0, optimizer: Optional[dict] = None) -> str:
+    """``global_step`` seeds the native dropout stream and indexes the learning-rate schedule: restoring it keeps
+    the masks of a resumed run from replaying those of the first epochs and continues the schedule.  ``optimizer``:
+    the run's optimizer options (plain numbers / strings), compared on load."""
     blob = {"params": params.detach().cpu(), "epoch": int(epoch), "model": model, "dtype": dtype,
             "global_step": int(global_step)}
+    if optimizer is not None:
+        blob["optimizer"] = dict(optimizer)
     if momentum is not None:
         blob["momentum"] = momentum.detach().cpu()
     tmp = path + ".tmp"

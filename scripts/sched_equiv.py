@@ -9,6 +9,9 @@ rank's "all-reduced" gradient is its own): they must equal a local run at half t
 (x0.5 is exact in binary floating point).
 ``_k<k>`` variants run the steps as ONE k-step graph (run_steps), whose steps may leave the aux
 branch join to the next step's head; they must equal the same number of single-step graphs.
+``--weight_decay`` / ``--nesterov`` / ``--lr_table a,b,c`` turn the optimizer options on (default: off, the digests
+of the variants above are unchanged).  With weight decay the ``w2`` == ``local_halflr`` identity no longer holds
+(the decay term is not scaled by 1/W); with Nesterov and a table alone it does.
 Usage: python scripts/sched_equiv.py [--model mlp|lenet5] [--dtype bf16|fp32] [--batch B] VARIANT [VARIANT ...]
   VARIANT = {local,local_halflr,join,split,overlap}[_g<groups>][_b<blocks>][_w2][_k<k>][_t<rows>]   (overlap: LeNet,
   world-1 one-shot; _t<rows>: one more step of a partial batch of <rows> rows after the full ones, eager launch;
@@ -37,6 +40,9 @@ ap.add_argument("--batch", type=int, default=512)
 ap.add_argument("--steps", type=int, default=4)
 ap.add_argument("--model", default="lenet5", choices=["lenet5", "mlp"])
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+ap.add_argument("--weight_decay", type=float, default=0.0)
+ap.add_argument("--nesterov", action="store_true")
+ap.add_argument("--lr_table", default=None, help="comma-separated per-step learning rates (halved for local_halflr)")
 ap.add_argument("--dump", default=None, help="also save each variant's parameters to DUMP.<variant>.pt")
 a = ap.parse_args()
 N = max(4096, a.batch * (a.steps + 1))  # (4096 for the default shapes: their digests are unchanged)
@@ -52,9 +58,16 @@ for v in a.variants:
     blocks, w2, k = int(m.group(3) or 0), bool(m.group(4)), int(m.group(5) or 0)
     tail_rows = int(m.group(6) or 0)
     lr = 0.025 if kind == "local_halflr" else 0.05
+    opts = {}  # (only what was asked for: the default variants construct the trainer as before)
+    if a.weight_decay:
+        opts["weight_decay"] = a.weight_decay
+    if a.nesterov:
+        opts["nesterov"] = True
+    if a.lr_table:
+        opts["lr_schedule"] = [float(t) * (0.5 if kind == "local_halflr" else 1.0) for t in a.lr_table.split(",")]
     torch.manual_seed(0)
     tr = NativeTrainer(a.model, a.dtype, a.batch, torch.from_numpy(x.reshape(-1, 784)), torch.from_numpy(y),
-                       lr=lr, momentum=0.9, dropout=0.0, init=build_model(a.model))
+                       lr=lr, momentum=0.9, dropout=0.0, init=build_model(a.model), **opts)
     if kind in ("join", "split"):
         tr.attach_comm(C.RcclComm(C.RcclComm.make_unique_id(), 0, 1, 0), 2 if w2 else 1, plan=kind,
                        bwd_blocks=blocks)
